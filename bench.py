@@ -7,6 +7,8 @@ torch-mode arithmetic by default).  Inputs are resident in HBM before the timed 
 
   python bench.py [--gpus N --steps K --warmup W]          # default: BASELINE config 3, 64 clients x 1e9 params;
                                                            # N > 1: starts N rank processes itself (launch_ranks)
+  python bench.py --full ...                               # the same, then everything else the line can carry (below)
+  python bench.py --dump-outputs DIR ...                   # the last timed step's results as DIR/<name>.npy
   torchrun --nproc-per-node N bench.py --gpus N ...        # the same N ranks under torchrun (WORLD_SIZE set)
   python bench.py --config {2,3,4,5}                       # BASELINE.json configs[1..4] (presets below)
 
@@ -14,7 +16,10 @@ Scaling.  The path shards by parameter bucket:
   weak   (configs 2, 3 -- single-GPU configs): every rank aggregates its own P-param bucket of the K clients
   strong (configs 4, 5 -- "sharded across 8", "1->8 GPUs"): a fixed global model of P params is split by
          sharding.bucket_ranges(P, N); rank r aggregates bucket r of every client.
-After the main measurement the default run also measures, in the same process, BASELINE configs 5 and 4 under
+A plain run does what the headline figure needs and no more: stage the workload, warm up, time --steps aggregations,
+write --dump-outputs, print the line.  Everything below is measured or checked only with ``--full`` (an ``--also``
+list given explicitly is still run as asked).
+After the main measurement the ``--full`` run also measures, in the same process, BASELINE configs 5 and 4 under
 strong scaling (``--also``; config 4 needs >= 2 GPUs: 358 GB of client updates do not fit one 288 GB HBM), and
 config 4 once more as a multi-GPU server would ingest it ("4x": client g's whole update on GPU g mod N, RCCL
 all-to-all of the buckets overlapped with the kernels, nvflare_amd/client_shards.py; serial and overlapped device
@@ -29,9 +34,16 @@ ranks of the barrier+synchronize bracketed wall time (P_total = P*N weak, P stro
 algorithmic bytes of one aggregation on one GPU (4*K*P_gpu + 4*P_gpu, or + the epilogue's state bytes) over
 its device time measured with HIP events on the stream the kernels run on (one aggregation =
 roofline.launches_per_step launches of the burst kernel; launch_us_avg is the per-launch time a rocprofv3
---stats average compares with).  cpu_baseline times the oracle restatement (torch CPU ops) on a bounded
-sample of the same workload, and the same leg spot-checks sampled device outputs bit-exactly against the
+--stats average compares with).  With ``--full``, cpu_baseline times the oracle restatement (torch CPU ops) on a
+bounded sample of the same workload, and the same leg spot-checks sampled device outputs bit-exactly against the
 oracle (test infrastructure; never the measured path).
+
+``--dump-outputs DIR`` writes what the main entry's last timed step left in its result buffers as float32
+``DIR/<name>.npy`` (``aggregate``; with a fused server update ``params`` and the optimizer's ``state1`` / ``state2``;
+``<name>_rank<r>.npy`` per rank at N > 1): the whole array up to DUMP_CHUNKS x DUMP_CHUNK elements, else that many
+elements in runs of DUMP_CHUNK at positions drawn from --seed (the first and the last run always).  The inputs come
+from the counter-hash generator keyed by --seed, so two runs with the same arguments dump the same elements of
+the same computation.
 """
 
 from __future__ import annotations
@@ -67,6 +79,8 @@ HOST_SHARDED = 21  # --also token "2s": the same round in ONE process over all N
 WATCHDOG_S = 240.0  # each guarded entry's limit: a stuck collective must not cost the measured line
 EPI_STATE_BYTES = {"none": 4.0, "add_base": 8.0, "sgd": 16.0}  # per param beyond the 4*K client reads; else 24
 HEADROOM = 2 << 30  # device bytes left free beside a workload (runtime, gather buffers)
+DUMP_CHUNK = 1 << 16  # --dump-outputs: elements per sampled run
+DUMP_CHUNKS = 64  # runs per dumped array: 4 Mi elements = 16 MiB of float32 each, three arrays at most
 
 
 def parse(argv=None):
@@ -74,6 +88,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the spot check "
+                         "against the oracle, the CPU baseline, the --also entries, the hand-out pull and the GPU "
+                         "state samples")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the main entry's last timed step as DIR/<name>.npy (float32; a seeded "
+                         "sample of arrays beyond 4 Mi elements)")
     ap.add_argument("--config", type=int, choices=sorted(PRESETS), default=3,
                     help="BASELINE.json workload preset (clients, params, epilogue, scaling); flags below override")
     ap.add_argument("--clients", type=int, default=None)
@@ -87,7 +108,7 @@ def parse(argv=None):
                          "2h = config 2 from host-resident updates to a host result, PCIe included, every rank / "
                          "2s = the same round in one process over all N GPUs' parameter buckets; "
                          "2 = config 2 device-resident (weak); "
-                         "'auto' = 2,5,4,2h,2s,4x for the default config 3 run; 'none')")
+                         "'auto' = 2,5,4,2h,2s,4x for the default config 3 run with --full, else none; 'none')")
     ap.add_argument("--client-sharded-params", type=float, default=None,
                     help="model size of the 4x entry (default: config 4's 350M; smaller for one-GPU rehearsals)")
     ap.add_argument("--host-resident-params", type=float, default=None,
@@ -133,7 +154,7 @@ def parse(argv=None):
                    for f in ("--clients", "--params", "--global-params", "--scaling", "--epilogue"))
     args.preset_exact = not explicit
     if args.also == "auto":
-        args.also = "2,5,4,2h,2s,4x" if (args.config == 3 and not explicit) else "none"
+        args.also = "2,5,4,2h,2s,4x" if (args.full and args.config == 3 and not explicit) else "none"
     tokens = {"4x": CLIENT_SHARDED, "2h": HOST_RESIDENT, "2s": HOST_SHARDED}
     args.also = [] if args.also in ("", "none") else [tokens.get(x.strip()) or int(x) for x in args.also.split(",")]
     return args
@@ -629,6 +650,31 @@ def wait_for_rank0(world, rank, key, timeout_s=1800.0):
         store.wait([key], datetime.timedelta(seconds=timeout_s))
 
 
+def dump_spans(P, seed):
+    """[(first element, elements)] of the --dump-outputs sample of a P-element array: all of it up to DUMP_CHUNKS runs
+    of DUMP_CHUNK elements, else that many runs at positions drawn from the seed, the first and the last run among
+    them (the last run holds the array's tail)."""
+    if P <= DUMP_CHUNK * DUMP_CHUNKS:
+        return [(0, P)]
+    n_runs = -(-P // DUMP_CHUNK)
+    picked = np.random.default_rng(seed).choice(n_runs - 2, DUMP_CHUNKS - 2, replace=False) + 1
+    runs = np.sort(np.concatenate([picked, [0, n_runs - 1]]))
+    return [(int(r) * DUMP_CHUNK, min(DUMP_CHUNK, P - int(r) * DUMP_CHUNK)) for r in runs]
+
+
+def dump_outputs(args, ctx, world, rank, P, arrays):
+    """Write this rank's result buffers ([(name, device buffer of P fp32)]) to --dump-outputs as float32 .npy."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    spans = dump_spans(P, args.seed)
+    for name, buf in arrays:
+        host = np.empty(sum(n for _, n in spans), dtype=np.float32)
+        at = 0
+        for lo, n in spans:
+            ctx.d2h(host[at:at + n], buf.ptr + 4 * lo)
+            at += n
+        np.save(os.path.join(args.dump_outputs, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), host)
+
+
 def kernel_name(K, epilogue, variant):
     # fewer client reads per launch than fedavg_capi.cpp's kBurstMinClients / kEpiBurstMinClients take the
     # per-tile-store kernels
@@ -651,8 +697,9 @@ def kernel_name(K, epilogue, variant):
                if K >= 32 and not variant & 64 else "8 register- + 4 LDS-held tiles per block per launch)"))
 
 
-def run_workload(args, ctx, world, rank, K, P_spec, scaling, epilogue, baseline, seed, min_warmup_s=0.0):
-    """Stage one workload in HBM, time args.steps aggregations after args.warmup, spot-check, free it.
+def run_workload(args, ctx, world, rank, K, P_spec, scaling, epilogue, baseline, seed, min_warmup_s=0.0, dump=False):
+    """Stage one workload in HBM, time args.steps aggregations after args.warmup, write --dump-outputs (``dump``: the
+    main entry), with --full spot-check it and time the hand-out pull, free it.
 
     Returns a dict (every rank) or, when the workload does not fit every rank's device, {"skipped": reason}."""
     from nvflare_amd import _native as N
@@ -743,7 +790,12 @@ def run_workload(args, ctx, world, rank, K, P_spec, scaling, epilogue, baseline,
         wall = max_over_ranks(world, t1 - t0)
         kernel_ms = ev_ms / args.steps
         kernel_ms_max = max_over_ranks(world, kernel_ms)
-        sc = spot_check(args, ctx, K, P, col0, op, epilogue, state if epi is not None else [out], n_step[0], seed)
+        if dump and args.dump_outputs:
+            names = {"none": ["aggregate"], "add_base": ["weights"]}.get(epilogue, ["params", "state1", "state2"])
+            dump_outputs(args, ctx, world, rank, P, list(zip(names, state)))
+        sc = None
+        if args.full:
+            sc = spot_check(args, ctx, K, P, col0, op, epilogue, state if epi is not None else [out], n_step[0], seed)
         if sc is not None and world > 1:  # every rank checks its own bucket; the counts are summed
             sampled, mism = sum_over_ranks(world, [sc["sampled"], sc["mismatches"]])
             sc.update(sampled=sampled, mismatches=mism, ranks=world)
@@ -751,7 +803,7 @@ def run_workload(args, ctx, world, rank, K, P_spec, scaling, epilogue, baseline,
                "wall": wall, "kernel_ms": kernel_ms, "kernel_ms_max": kernel_ms_max,
                "launches_per_step": launches_per_step, "spot_check": sc, "op": op,
                "gpu_state": sampler.summary() if sampler is not None else None}
-        if epi is not None and epilogue != "add_base":
+        if args.full and epi is not None and epilogue != "add_base":
             res["handout_pull"] = handout_pull(args, ctx, world, state[0], P)
     finally:
         slab.close()
@@ -1148,14 +1200,14 @@ def main(argv=None):
     ctx = DeviceContext.get(local)
     ctx.set_launch(args.blocks_per_cu, args.unroll)
     ctx.set_variant(args.variant)
-    args.gpu_monitor = gpu_monitor(local)
+    args.gpu_monitor = gpu_monitor(local) if args.full else None
     state_before = gpu_snapshot(args) if rank == 0 else None
     K = args.clients
     label = (PRESET_NAMES[args.config] if args.preset_exact
              else f"custom (preset {args.config} overridden: {K} clients x {args.params} params, {args.epilogue})")
     t_main = time.perf_counter()
     main_res = run_workload(args, ctx, world, rank, K, args.params, args.scaling, args.epilogue, baseline=False,
-                            seed=args.seed)
+                            seed=args.seed, dump=True)
     main_s = time.perf_counter() - t_main
     if "skipped" in main_res:
         raise SystemExit(f"rank {rank}: workload {main_res['skipped']}")
@@ -1213,8 +1265,8 @@ def main(argv=None):
             "pct_hbm_peak": s["pct_hbm_peak"],
             "roofline": s["roofline"],
             "cpu_baseline": None,  # rank 0, after every GPU entry (below)
-            "elapsed_s": round(main_s, 2),  # the main entry's wall time: fill, warmup, steps, spot check
-            "gpu_state": {"before": state_before, "main_timed": main_res.get("gpu_state")},
+            "elapsed_s": round(main_s, 2),  # the main entry's wall time: fill, warmup, steps, dump, spot check
+            "gpu_state": {"before": state_before, "main_timed": main_res.get("gpu_state")} if args.full else None,
         }
         if main_res.get("handout_pull"):
             line["handout_pull"] = main_res["handout_pull"]
@@ -1232,7 +1284,7 @@ def main(argv=None):
         dog = None
     # the CPU baseline on rank 0 at EVERY N, after all GPU entries so it perturbs none of them;
     # the other ranks sleep on the rendezvous store meanwhile (wait_for_rank0), not in a spinning collective
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         t_cpu = time.perf_counter()
         try:
             line["cpu_baseline"] = cpu_baseline(args, K, min(args.params, main_res["P"]), main_res["op"])
@@ -1242,7 +1294,8 @@ def main(argv=None):
             line["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
     wait_for_rank0(world, rank, "nvflare_amd_bench_cpu_baseline_done")
     if rank == 0:
-        line["gpu_state"]["after"] = gpu_snapshot(args)
+        if args.full:
+            line["gpu_state"]["after"] = gpu_snapshot(args)
         if also:
             line["also"] = also
         state["printed"] = True

@@ -1,4 +1,4 @@
-"""bench.py's default run at N = 1 -- the line the driver records every round -- on the fake device:
+"""bench.py's ``--full`` run at N = 1 on the fake device (the plain run: the last tests here):
 besides config 3 (the value) it carries config 2 device-resident, config 5 with the FedOpt hand-out pull timed, and,
 because config 4 does not fit one GPU, ONE GPU's share of the 8-GPU split of config 4 labelled as the share (instead of
 a skip); the CPU baseline runs after every GPU entry, and every entry records the GPU state it ran at (here: not
@@ -51,7 +51,7 @@ def test_default_run_at_one_gpu(monkeypatch, undo_install):
     monkeypatch.setattr(ctx, "total_bytes", bench.HEADROOM + (8 << 20))
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--steps", "2", "--warmup", "1", "--host-resident-params", "10001", "--spot-check", "64",
+        bench.main(["--full", "--steps", "2", "--warmup", "1", "--host-resident-params", "10001", "--spot-check", "64",
                     "--cpu-baseline-s", "0.2", "--cpu-sample-params", "4096"])
     lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -83,3 +83,80 @@ def test_default_run_at_one_gpu(monkeypatch, undo_install):
     cb = d["cpu_baseline"]
     assert cb["value"] > 0 and cb["n_gpus_in_run"] == 1
     assert set(d["gpu_state"]) == {"before", "main_timed", "after"}
+
+
+def _plain_line(bench, argv):
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        bench.main(argv)
+    lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_times_the_steps_and_dumps_its_outputs(monkeypatch, undo_install, tmp_path, oracle):
+    """Without --full the run stages, warms up, times --steps steps, writes --dump-outputs and prints the line: no spot
+    check, no CPU baseline, no other entries, no GPU state.  The dumped aggregate is the oracle's bit for bit, a second
+    run with the same arguments dumps the same bytes, and the fused Adam run dumps the parameter and both moments."""
+    import numpy as np
+
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    bench = install(0, 1)
+    monkeypatch.setattr(bench, "dist_setup", lambda args: (1, 0, 0))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("the CPU baseline ran without --full"))
+    monkeypatch.setattr(bench, "spot_check", lambda *a, **k: pytest.fail("the spot check ran without --full"))
+    monkeypatch.setattr(bench, "handout_pull", lambda *a, **k: pytest.fail("the hand-out pull ran without --full"))
+    monkeypatch.setattr(bench, "gpu_monitor", lambda *a, **k: pytest.fail("the GPU monitor started without --full"))
+    d = _plain_line(bench, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["metric"] == bench.METRIC
+    assert "also" not in d and "spot_check" not in d and d["cpu_baseline"] is None and d["gpu_state"] is None
+    small = small_presets(1)[3]
+    K, P = small["clients"], small["params"]
+    assert d["value"] == pytest.approx(4.0 * K * P / (d["ms_per_step"] / 1e3) / 2**30, rel=2e-3, abs=0.006)
+    got = np.load(tmp_path / "a" / "aggregate.npy")
+    assert got.dtype == np.float32 and got.shape == (P,)
+    cols = np.arange(P, dtype=np.uint64)
+    want = oracle.fedavg_c([oracle.synth_values(1000, k, cols) for k in range(K)], oracle.synth_weights(K),
+                           oracle.MODE_TORCH)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    _plain_line(bench, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "b")])
+    assert sorted(os.listdir(tmp_path / "b")) == ["aggregate.npy"]
+    assert (tmp_path / "a" / "aggregate.npy").read_bytes() == (tmp_path / "b" / "aggregate.npy").read_bytes()
+    _plain_line(bench, ["--config", "5", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "c")])
+    assert sorted(os.listdir(tmp_path / "c")) == ["params.npy", "state1.npy", "state2.npy"]
+    P5 = small_presets(1)[5]["params"]
+    p, m, v = (np.load(tmp_path / "c" / f"{n}.npy") for n in ("params", "state1", "state2"))
+    assert p.dtype == m.dtype == v.dtype == np.float32 and p.shape == m.shape == v.shape == (P5,)
+    d5 = oracle.fedavg_c([oracle.synth_values(1000, k, np.arange(P5, dtype=np.uint64)) for k in range(64)],
+                         oracle.synth_weights(64), oracle.MODE_TORCH)
+    p_w = oracle.synth_values(1007, 0, np.arange(P5, dtype=np.uint64))
+    m_w, v_w = np.zeros_like(p_w), np.zeros_like(p_w)
+    args5 = bench.parse(["--config", "5"])
+    for s in (1, 2, 3):  # one warmup step and two timed ones
+        oracle.epilogue_apply(d5, oracle.EPI_ADAM, p=p_w, m=m_w, v=v_w, step=float(s),
+                              torch_cpu_sqrt=bench.sqrt_mode(args5), **bench.ADAM_HP)
+    for got5, want5 in ((p, p_w), (m, m_w), (v, v_w)):
+        assert np.array_equal(got5.view(np.uint32), want5.view(np.uint32))
+
+
+def test_dump_sample_is_fixed_by_the_seed_and_bounded():
+    """Arrays beyond DUMP_CHUNKS x DUMP_CHUNK elements are sampled: the same sorted, disjoint, in-range runs for the same
+    seed, the first run and the array's tail among them, 16 MiB of float32 per array (three arrays at most: under the
+    64 MB a dump may take)."""
+    import bench
+
+    limit = bench.DUMP_CHUNK * bench.DUMP_CHUNKS
+    assert 3 * 4 * limit <= 64 * 10**6
+    for P in (1, 4099, limit):
+        assert bench.dump_spans(P, 1000) == [(0, P)]
+    for P in (limit + 1, 10**9, 10**9 + 3, 2**31 + 5):
+        spans = bench.dump_spans(P, 1000)
+        assert spans == bench.dump_spans(P, 1000) and len(spans) == bench.DUMP_CHUNKS
+        assert spans[0][0] == 0 and spans[-1][0] + spans[-1][1] == P
+        assert all(0 < n <= bench.DUMP_CHUNK for _, n in spans)
+        assert all(a[0] + a[1] <= b[0] for a, b in zip(spans, spans[1:]))
+        assert sum(n for _, n in spans) <= limit
+    assert bench.dump_spans(10**9, 1000) != bench.dump_spans(10**9, 1001)

@@ -109,9 +109,11 @@ def test_bench_presets_follow_baseline():
     explicit overrides turn that off."""
     import bench
 
-    a = bench.parse([])
+    a = bench.parse(["--full"])
     assert (a.clients, a.params, a.epilogue, a.scaling, a.also) == \
         (64, 10**9, "none", "weak", [2, 5, 4, bench.HOST_RESIDENT, bench.HOST_SHARDED, bench.CLIENT_SHARDED])
+    plain = bench.parse([])  # without --full: the same workload and nothing after it
+    assert (plain.clients, plain.params, plain.epilogue, plain.scaling, plain.also) == (64, 10**9, "none", "weak", [])
     assert bench.parse(["--also", "4x,5"]).also == [bench.CLIENT_SHARDED, 5]
     assert bench.parse(["--also", "2h"]).also == [bench.HOST_RESIDENT]
     assert bench.parse(["--also", "2s,2h"]).also == [bench.HOST_SHARDED, bench.HOST_RESIDENT]

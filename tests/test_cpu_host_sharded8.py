@@ -75,8 +75,8 @@ def test_a_stalled_device_ends_the_2s_entry_through_the_watchdog(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     t0 = time.monotonic()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--host-resident-params", "40001", "--spot-check", "64", "--watchdog-s", "8",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "2",
+                        "--warmup", "1", "--host-resident-params", "40001", "--spot-check", "64", "--watchdog-s", "8",
                         "--cpu-baseline-s", "0.2", "--cpu-sample-params", "4096"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert time.monotonic() - t0 < 200
